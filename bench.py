@@ -20,6 +20,11 @@ rank as in round 1.
 Timing: W untimed warmup steps, then exactly K steps bracketed by
 barrier+synchronize on both sides, elapsed MAX-reduced over ranks, ONE
 JSON line from rank 0 with the whole-job aggregate tokens/s.
+
+--dump-outputs DIR: after the timed window, rank 0 writes what the last
+timed step produced as DIR/<name>.npy (see _dump_outputs). Inputs are
+seeded, so two builds run with the same arguments can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -27,6 +32,11 @@ import argparse
 import json
 import os
 import time
+
+# per-array cap on the sampled flat-buffer elements written by
+# --dump-outputs: 3 fp32 arrays x 4M = 48 MB, under the 64 MB budget
+DUMP_SAMPLE = 4 << 20
+DUMP_SEED = 0
 
 
 def _setup_tunableop(local_rank: int):
@@ -79,7 +89,15 @@ def _parse_args(argv=None):
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--bare", action="store_true",
                     help="skip the Ray runtime: raw torchrun DDP ranks")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs:
+        # Ray worker actors do not share the driver's cwd
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
 
 
 def _resolve_batch(args) -> int:
@@ -147,7 +165,36 @@ def _train_core(args, device, rank: int, world: int):
         t = torch.tensor([elapsed], device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, opt)
     return elapsed, float(loss.item())
+
+
+def _dump_outputs(out_dir: str, loss, opt):
+    """What a timed step hands back: its loss, and the weights and AdamW
+    moments it updated (the moments carry the gradients, which the step
+    zeroes at its end). The flat buffers are gathered at a fixed seeded
+    set of at most DUMP_SAMPLE indices, the same for every run of the
+    same model."""
+    import numpy as np
+    import torch
+
+    numel = opt.master.numel()
+    if numel <= DUMP_SAMPLE:
+        idx = torch.arange(numel)
+    else:
+        gen = torch.Generator().manual_seed(DUMP_SEED)
+        idx = torch.randint(0, numel, (DUMP_SAMPLE,), generator=gen).sort().values
+    idx = idx.to(opt.master.device)
+    arrays = {
+        "loss": loss.detach().double().reshape(1),
+        "params": opt.master[idx],
+        "exp_avg": opt.m[idx],
+        "exp_avg_sq": opt.v[idx],
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def _emit(args, world: int, elapsed: float, final_loss: float):

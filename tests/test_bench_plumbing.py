@@ -10,14 +10,14 @@ import subprocess
 import sys
 
 
-def test_via_ray_torchrun_cpu_2ranks():
+def test_via_ray_torchrun_cpu_2ranks(tmp_path):
     env = dict(os.environ, ANTRAY_BENCH_CPU="1")
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29721", "bench.py", "--gpus", "2",
          "--model", "llama-tiny", "--seq", "64", "--batch", "2",
-         "--steps", "2", "--warmup", "1"],
+         "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
         capture_output=True, text=True, timeout=600, env=env,
         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -28,6 +28,14 @@ def test_via_ray_torchrun_cpu_2ranks():
     assert rec["config"]["parallelism"] == "dp2"
     assert rec["config"]["via"] == "ray-train"
     assert rec["value"] > 0
+    # --dump-outputs: the last timed step's loss + updated optimizer state
+    import numpy as np
+
+    dumped = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(dumped) == {"loss", "params", "exp_avg", "exp_avg_sq"}
+    assert all(a.dtype in (np.float32, np.float64) for a in dumped.values())
+    assert sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    assert abs(float(dumped["loss"][0]) - rec["config"]["final_loss"]) < 1e-3
 
 
 def test_bare_mode_flag():

@@ -15,6 +15,8 @@ import time
 
 import pytest
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 def _free_port():
     s = socket.socket()
@@ -238,7 +240,7 @@ def test_driver_death_cleans_up_actors(tmp_path):
         """)
         proc = subprocess.Popen([sys.executable, "-c", script],
                                 stdout=subprocess.PIPE, text=True,
-                                cwd="/root/repo")
+                                cwd=REPO)
         assert proc.stdout.readline().startswith("READY")
         proc.kill()
         proc.wait(timeout=10)

@@ -1,9 +1,12 @@
 """Ray Serve parity tests: deployments, handles, composition, HTTP proxy,
 batching, autoscaling policy math, status/delete."""
 import asyncio
+import os
 import time
 
 import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -708,7 +711,7 @@ def test_request_timeout(serve_mod):
         ray.shutdown()
     """)
     out = subprocess.run([sys.executable, "-c", script], capture_output=True,
-                         text=True, timeout=180, cwd="/root/repo")
+                         text=True, timeout=180, cwd=REPO)
     assert "STATUS 408" in out.stdout, out.stdout[-800:] + out.stderr[-800:]
 
 

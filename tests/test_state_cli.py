@@ -4,6 +4,8 @@ import time
 
 import pytest
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 @pytest.fixture(scope="module")
 def ray_mod():
@@ -154,7 +156,7 @@ def test_cli_logs_health_stack_drain(ray_mod):
     import sys
 
     env = dict(os.environ)
-    env["PYTHONPATH"] = "/root/repo"
+    env["PYTHONPATH"] = REPO
 
     def run(*args):
         return subprocess.run(

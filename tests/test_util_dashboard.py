@@ -1,9 +1,12 @@
 """Tests: ray.util.queue / ActorPool / metrics, and the dashboard REST head."""
 import json
+import os
 import time
 import urllib.request
 
 import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -358,8 +361,6 @@ def test_logging_config_propagates_to_workers():
     import sys
 
     code = r"""
-import sys
-sys.path.insert(0, "/root/repo")
 import ray
 ray.init(num_cpus=1, logging_config=ray.LoggingConfig(encoding="JSON"))
 
@@ -377,7 +378,7 @@ print("FORMATTED::" + out)
 ray.shutdown()
 """
     r = subprocess.run([sys.executable, "-c", code], capture_output=True,
-                       text=True, timeout=180)
+                       text=True, timeout=180, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines()
             if ln.startswith("FORMATTED::")][0]
