@@ -46,6 +46,14 @@ void launch_attn_decode(const void*, const void*, const void*, void*, float*,
 void launch_rope_cache_write(void*, void*, void*, const int*, const float*,
                              const float*, int, int, int, int, long, long,
                              long, hipStream_t);
+void launch_attn_decode_paged(const void*, const void*, const void*, void*,
+                              float*, const int*, const int*, int, int, int,
+                              int, int, int, int, long, long, long, long,
+                              float, void*);
+void launch_rope_cache_write_paged(void*, void*, void*, const int*,
+                                   const int*, const float*, const float*,
+                                   int, int, int, int, int, int, int, int,
+                                   long, long, long, hipStream_t);
 void launch_cast_affine_u8(const void*, void*, const float*, const float*,
                            long, int, int, int, void*);
 void launch_cast_affine_f32(const void*, void*, const float*, const float*,
@@ -454,6 +462,131 @@ torch::Tensor decode_step_attn(torch::Tensor qkv, torch::Tensor ck,
   return o;
 }
 
+// ---- paged KV cache (layout: csrc/kernels/attention_decode.hip header) ----
+//
+// One layer's pools are [n_pages, Hk, P, D] bf16, contiguous; the block
+// table is int32 [B, W] on device, W * P = static per-sequence capacity.
+
+namespace {
+
+void check_paged(const torch::Tensor& kp, const torch::Tensor& vp,
+                 const torch::Tensor& table, const torch::Tensor& lens,
+                 int64_t B) {
+  TORCH_CHECK(kp.is_cuda() && kp.scalar_type() == torch::kBFloat16 &&
+              vp.is_cuda() && vp.scalar_type() == torch::kBFloat16,
+              "k/v pools must be bf16 on GPU");
+  TORCH_CHECK(kp.dim() == 4 && kp.is_contiguous() && vp.is_contiguous() &&
+              kp.sizes() == vp.sizes(),
+              "k/v pools must be contiguous [n_pages,Hk,P,D] of one shape");
+  TORCH_CHECK(kp.size(3) == 128, "paged decode: D must be 128");
+  TORCH_CHECK(kp.size(2) % 16 == 0 && kp.size(2) > 0,
+              "paged decode: page size P must be a multiple of 16");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == torch::kInt32 &&
+              table.dim() == 2 && table.is_contiguous(),
+              "block_table must be contiguous int32 [B, W] on device");
+  TORCH_CHECK(table.size(0) == B, "block_table must have one row per seq");
+  TORCH_CHECK(lens.is_cuda() && lens.scalar_type() == torch::kInt32 &&
+              lens.is_contiguous() && lens.numel() == B,
+              "lens must be int32 [B] on device");
+}
+
+// C from the STATIC table capacity (graph shapes cannot depend on lens)
+int paged_chunks(int B, int Hk, long cap) {
+  static const long wg_target = [] {
+    const char* e = getenv("ANTRAY_DEC_WGS");
+    return e ? atol(e) : 1024L;
+  }();
+  return (int)std::min<long>(std::max<long>(1, wg_target / std::max(1, B * Hk)),
+                             std::max<long>(1, (cap + 127) / 128));
+}
+
+torch::Tensor run_paged_decode(const torch::Tensor& q, long qbs,
+                               const torch::Tensor& kp,
+                               const torch::Tensor& vp,
+                               const torch::Tensor& table,
+                               const torch::Tensor& lens, int B, int Hq,
+                               double scale) {
+  const int Hk = kp.size(1), P = kp.size(2), D = kp.size(3);
+  const int W = table.size(1);
+  const int C = paged_chunks(B, Hk, (long)W * P);
+  auto o = torch::empty({B, Hq, D}, q.options());
+  torch::Tensor part;
+  float* part_ptr = nullptr;
+  if (C > 1) {
+    part = torch::empty({(long)B * Hq * C * (D + 2)},
+                        q.options().dtype(torch::kFloat32));
+    part_ptr = part.data_ptr<float>();
+  }
+  launch_attn_decode_paged(q.data_ptr(), kp.data_ptr(), vp.data_ptr(),
+                           o.data_ptr(), part_ptr, lens.data_ptr<int>(),
+                           table.data_ptr<int>(), W, P, (int)kp.size(0), B,
+                           Hq, Hk, C, kp.stride(0), kp.stride(1),
+                           kp.stride(2), qbs, (float)scale,
+                           (void*)cur_stream());
+  return o;
+}
+
+}  // namespace
+
+// Paged flash-decode: q [B, Hq, D]; k/v pools [n_pages, Hk, P, D];
+// block_table int32 [B, W]; lens int32 [B] on device. A length above the
+// table capacity W * P is clamped to it on device (lens is not read on the
+// host, so the call never synchronizes). Returns o [B, Hq, D] bf16.
+torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor k_pool,
+                                torch::Tensor v_pool,
+                                torch::Tensor block_table, torch::Tensor lens,
+                                double scale) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, "q bf16 gpu");
+  TORCH_CHECK(q.dim() == 3 && q.is_contiguous(), "q must be [B,Hq,D] contig");
+  const int B = q.size(0), Hq = q.size(1);
+  check_paged(k_pool, v_pool, block_table, lens, B);
+  const int Hk = k_pool.size(1);
+  TORCH_CHECK(q.size(2) == k_pool.size(3), "q/pool head_dim mismatch");
+  TORCH_CHECK(Hq % Hk == 0 && Hq / Hk <= 8,
+              "attn_decode_paged: Hq/Hk must be <=8");
+  return run_paged_decode(q, (long)Hq * q.size(2), k_pool, v_pool,
+                          block_table, lens, B, Hq, scale);
+}
+
+// Paged device-pos decode step (graph-capturable): rope q/k, write the new
+// K/V row at page block_table[b, pos/P], slot pos%P (pos = lens[b]-1), then
+// paged flash-decode. qkv: [B, 1, (Hq+2Hk)*D] or [B, (Hq+2Hk)*D].
+torch::Tensor decode_step_attn_paged(torch::Tensor qkv, torch::Tensor k_pool,
+                                     torch::Tensor v_pool,
+                                     torch::Tensor block_table,
+                                     torch::Tensor lens, torch::Tensor cos_t,
+                                     torch::Tensor sin_t, int64_t Hq,
+                                     int64_t Hk, double scale) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 &&
+              qkv.is_contiguous(), "qkv must be contiguous bf16 gpu");
+  const int B = block_table.size(0);
+  check_paged(k_pool, v_pool, block_table, lens, B);
+  const int P = k_pool.size(2), D = k_pool.size(3);
+  const int W = block_table.size(1);
+  TORCH_CHECK(k_pool.size(1) == Hk, "pool Hk mismatch");
+  TORCH_CHECK(Hq % Hk == 0 && Hq / Hk <= 8,
+              "decode_step_paged: Hq/Hk must be <=8");
+  TORCH_CHECK(qkv.numel() == (long)B * (Hq + 2 * Hk) * D, "qkv shape");
+  TORCH_CHECK(cos_t.scalar_type() == torch::kFloat32 &&
+              sin_t.scalar_type() == torch::kFloat32 &&
+              cos_t.is_contiguous() && sin_t.is_contiguous() &&
+              cos_t.dim() == 2 && cos_t.size(1) == D / 2 &&
+              sin_t.sizes() == cos_t.sizes(),
+              "cos/sin must be f32 [S, D/2] contiguous");
+  // the rope table bounds the positions a caller can reach; the block
+  // table must be able to hold every one of them
+  TORCH_CHECK((long)W * P >= cos_t.size(0),
+              "block table capacity W*P must cover the rope table length");
+  launch_rope_cache_write_paged(
+      qkv.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+      lens.data_ptr<int>(), block_table.data_ptr<int>(),
+      cos_t.data_ptr<float>(), sin_t.data_ptr<float>(), B, (int)Hq, (int)Hk,
+      D, W, P, (int)k_pool.size(0), (int)cos_t.size(0), k_pool.stride(0),
+      k_pool.stride(1), k_pool.stride(2), cur_stream());
+  return run_paged_decode(qkv, (long)(Hq + 2 * Hk) * D, k_pool, v_pool,
+                          block_table, lens, B, (int)Hq, scale);
+}
+
 // Fused cast + per-channel affine: y = (x - shift) * scale. x u8 or f32;
 // out bf16 or f32. scale/shift: f32 tensors of numel 1 (scalar) or C
 // (= x's innermost dim). Data-plane collate hot path.
@@ -530,6 +663,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hq"), py::arg("hk"), py::arg("scale"));
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("T"), py::arg("scale"), py::arg("lens") = py::none());
+  m.def("attn_decode_paged", &attn_decode_paged, py::arg("q"),
+        py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+        py::arg("lens"), py::arg("scale"));
+  m.def("decode_step_attn_paged", &decode_step_attn_paged, py::arg("qkv"),
+        py::arg("k_pool"), py::arg("v_pool"), py::arg("block_table"),
+        py::arg("lens"), py::arg("cos"), py::arg("sin"), py::arg("hq"),
+        py::arg("hk"), py::arg("scale"));
   m.def("cast_affine", &cast_affine, py::arg("x"), py::arg("scale"),
         py::arg("shift"), py::arg("out_dtype"));
   m.def("nhwc_to_nchw", &nhwc_to_nchw, py::arg("x"), py::arg("scale"),

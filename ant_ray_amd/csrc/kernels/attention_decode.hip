@@ -20,6 +20,22 @@
 //     combine). C == 1 writes bf16 output directly and skips level 2.
 //
 // Supports per-sequence lengths (lens[b]) for ragged serve batches.
+//
+// PAGED variant (template PAGED = true): the cache is a page pool and a
+// per-sequence block table instead of one contiguous [B, Hk, Tmax, D]
+// region. Pool layout — the ONE definition used by the kernels, the
+// binding (csrc/hip_ops.cpp), the CPU reference (ops/reference.py) and the
+// block manager (llm/kv_blocks.py):
+//   K/V pool  [n_layers, n_pages, Hk, P, D] bf16 (the kernel sees one
+//             layer: [n_pages, Hk, P, D]; each (page, head) run is P*256 B
+//             contiguous),
+//   table     int32 [B, W]; key t of sequence b lives at page
+//             table[b, t / P], slot t % P. W * P is the static capacity.
+// P is a multiple of 16 (the key stride of the 16 lane-groups), and the
+// paged chunk split is 16-aligned, so all 16 groups cross a page boundary
+// on the same iteration and each group reads the table once per page it
+// enters. Page ids are clamped to [0, n_pages) and lengths to W * P, so a
+// bad table or length can never address outside the pool.
 #include <hip/hip_runtime.h>
 
 #include "common.hip.h"
@@ -38,28 +54,33 @@ typedef float floatx2 __attribute__((ext_vector_type(2)));
 // VGPRs and cap the kernel at 2 waves/SIMD; llama3-8b runs GQ=4 (~120
 // VGPRs -> 4 waves/SIMD, twice the latency hiding for the HBM-bound KV
 // walk). MAXOCC passes the matching __launch_bounds__ occupancy.
-template <int GQT, int MAXOCC>
+template <int GQT, int MAXOCC, bool PAGED>
 __global__ __launch_bounds__(256, MAXOCC) void attn_decode_kernel(
     const ushort_t* __restrict__ Q,   // [B, Hq, D] contiguous
-    const ushort_t* __restrict__ K,   // [B, Hk, Tmax, D] via strides
+    const ushort_t* __restrict__ K,   // [B, Hk, Tmax, D] via strides, or
+                                      // (PAGED) [n_pages, Hk, P, D]
     const ushort_t* __restrict__ V,   // same layout as K
     ushort_t* __restrict__ O,         // [B, Hq, D] bf16 (used when C == 1)
     float* __restrict__ PART,         // [B, Hq, C, D+2] f32 (when C > 1)
     const int* __restrict__ lens,     // [B] valid lengths (nullptr -> T)
     int T, int Hq, int Hk, int C,
-    long kb, long kh, long ks,        // K/V strides (elements)
+    long kb, long kh, long ks,        // K/V strides (elements); PAGED: kb
+                                      // is the page stride
     long qbs,                         // Q batch stride (Hq*D, or the fused
                                       // qkv row stride when q is a region)
-    float scale_log2) {
+    float scale_log2,
+    const int* __restrict__ table,    // PAGED: [B, W] page ids
+    int W, int P, int n_pages) {
   const int chunk = blockIdx.x;
   const int hk = blockIdx.y;
   const int b = blockIdx.z;
   constexpr int GA = GQT > 0 ? GQT : DEC_MAX_GQ;  // register-array bound
   const int GQ = GQT > 0 ? GQT : (Hq / Hk);
 
-  const int seq_len = lens ? lens[b] : T;
+  const int seq_len = PAGED ? min(lens[b], W * P) : (lens ? lens[b] : T);
   // chunk covers keys [c0, c1)
-  const int per_chunk = (seq_len + C - 1) / C;
+  int per_chunk = (seq_len + C - 1) / C;
+  if (PAGED) per_chunk = (per_chunk + 15) & ~15;  // page crossings uniform
   const int c0 = chunk * per_chunk;
   const int c1 = min(c0 + per_chunk, seq_len);
 
@@ -68,8 +89,22 @@ __global__ __launch_bounds__(256, MAXOCC) void attn_decode_kernel(
   const int gl = tid & 15;           // lane within group
   const int d0 = gl * 8;             // this lane's 8 dims
 
-  const ushort_t* Kp = K + (long)b * kb + (long)hk * kh;
-  const ushort_t* Vp = V + (long)b * kb + (long)hk * kh;
+  const ushort_t* Kp = K + (PAGED ? 0L : (long)b * kb) + (long)hk * kh;
+  const ushort_t* Vp = V + (PAGED ? 0L : (long)b * kb) + (long)hk * kh;
+  // PAGED: element offset of key t within Kp/Vp. Keys of one group only
+  // grow, so the table is read when t leaves the current page [pg0, pg0+P).
+  const int* trow = PAGED ? table + (long)b * W : nullptr;
+  int pg0 = -P;
+  long pg_off = 0;
+  auto key_off = [&](int t) -> long {
+    if (!PAGED) return (long)t * ks;
+    if (t >= pg0 + P) {
+      const int p = t / P;
+      pg0 = p * P;
+      pg_off = (long)min((unsigned)trow[p], (unsigned)(n_pages - 1)) * kb;
+    }
+    return pg_off + (long)(t - pg0) * ks;
+  };
 
   // Q fragments for the GQ query heads of this kv group (8 f32 per head)
   floatx8 qf[GA];
@@ -94,13 +129,15 @@ __global__ __launch_bounds__(256, MAXOCC) void attn_decode_kernel(
   ushortx8 kv, vv, kv_n, vv_n;
   const int key0 = c0 + group;
   if (key0 < c1) {
-    kv = *(const ushortx8*)(Kp + (long)key0 * ks + d0);
-    vv = *(const ushortx8*)(Vp + (long)key0 * ks + d0);
+    const long off = key_off(key0);
+    kv = *(const ushortx8*)(Kp + off + d0);
+    vv = *(const ushortx8*)(Vp + off + d0);
   }
   for (int key = key0; key < c1; key += 16) {
     if (key + 16 < c1) {
-      kv_n = *(const ushortx8*)(Kp + (long)(key + 16) * ks + d0);
-      vv_n = *(const ushortx8*)(Vp + (long)(key + 16) * ks + d0);
+      const long off = key_off(key + 16);
+      kv_n = *(const ushortx8*)(Kp + off + d0);
+      vv_n = *(const ushortx8*)(Vp + off + d0);
     }
     const floatx8 kf = bf8_to_f32x8(kv);
     const floatx8 vf = bf8_to_f32x8(vv);
@@ -199,20 +236,23 @@ extern "C" __global__ __launch_bounds__(128, 8) void attn_decode_combine_kernel(
   O[bh * DEC_D + d] = f2bf(o_sum / l_safe);
 }
 
-extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
-                                   void* o, float* part, const int* lens,
-                                   int B, int T, int Hq, int Hk, int C,
-                                   long kb, long kh, long ks, long qbs,
-                                   float scale, void* stream) {
+template <bool PAGED>
+static void launch_decode(const void* q, const void* k, const void* v,
+                          void* o, float* part, const int* lens,
+                          const int* table, int W, int P, int n_pages,
+                          int B, int T, int Hq, int Hk, int C, long kb,
+                          long kh, long ks, long qbs, float scale,
+                          void* stream) {
   const float scale_log2 = scale * 1.4426950408889634f;
   dim3 grid(C, Hk, B);
   const int GQ = Hq / Hk;
   const size_t lds = (size_t)16 * GQ * (DEC_D + 2) * sizeof(float);
 #define ANTRAY_DEC_LAUNCH(GQV, OCC)                                          \
-  hipLaunchKernelGGL((attn_decode_kernel<GQV, OCC>), grid, dim3(256), lds,   \
-                     (hipStream_t)stream, (const ushort_t*)q,                \
+  hipLaunchKernelGGL((attn_decode_kernel<GQV, OCC, PAGED>), grid, dim3(256), \
+                     lds, (hipStream_t)stream, (const ushort_t*)q,           \
                      (const ushort_t*)k, (const ushort_t*)v, (ushort_t*)o,   \
-                     part, lens, T, Hq, Hk, C, kb, kh, ks, qbs, scale_log2)
+                     part, lens, T, Hq, Hk, C, kb, kh, ks, qbs, scale_log2,  \
+                     table, W, P, n_pages)
   switch (GQ) {
     case 1: ANTRAY_DEC_LAUNCH(1, 4); break;
     case 2: ANTRAY_DEC_LAUNCH(2, 4); break;
@@ -225,4 +265,26 @@ extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
     hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(B * Hq), dim3(128), 0,
                        (hipStream_t)stream, part, (ushort_t*)o, C);
   }
+}
+
+extern "C" void launch_attn_decode(const void* q, const void* k, const void* v,
+                                   void* o, float* part, const int* lens,
+                                   int B, int T, int Hq, int Hk, int C,
+                                   long kb, long kh, long ks, long qbs,
+                                   float scale, void* stream) {
+  launch_decode<false>(q, k, v, o, part, lens, nullptr, 0, 0, 0, B, T, Hq,
+                       Hk, C, kb, kh, ks, qbs, scale, stream);
+}
+
+// Paged: k/v are one layer's pool [n_pages, Hk, P, D] (page stride kb,
+// head stride kh, slot stride ks); table int32 [B, W]; lens required.
+extern "C" void launch_attn_decode_paged(const void* q, const void* k,
+                                         const void* v, void* o, float* part,
+                                         const int* lens, const int* table,
+                                         int W, int P, int n_pages, int B,
+                                         int Hq, int Hk, int C, long kb,
+                                         long kh, long ks, long qbs,
+                                         float scale, void* stream) {
+  launch_decode<true>(q, k, v, o, part, lens, table, W, P, n_pages, B, W * P,
+                      Hq, Hk, C, kb, kh, ks, qbs, scale, stream);
 }

@@ -148,3 +148,84 @@ extern "C" void launch_rope_cache_write(void* qkv, void* ck, void* cv,
                      (ushort_t*)cv, lens, cos_t, sin_t, B, Hq, Hk, D, cb, ch,
                      cs);
 }
+
+// ---- paged variant -------------------------------------------------------
+//
+// Same step prep for a PAGED cache (layout documented at the top of
+// attention_decode.hip): position pos = lens[b] - 1 goes to page
+// table[b, pos / P], slot pos % P of the layer's pool [n_pages, Hk, P, D]
+// (page stride cp, head stride ch, slot stride cs). Positions outside the
+// table's W * P capacity or the rope table are not written, and page ids
+// are clamped into the pool, so no device value can send a write out of
+// bounds. Graph-capturable like the contiguous kernel.
+extern "C" __global__ void __launch_bounds__(256)
+rope_cache_write_paged_kernel(ushort_t* __restrict__ qkv,
+                              ushort_t* __restrict__ pk,
+                              ushort_t* __restrict__ pv,
+                              const int* __restrict__ lens,
+                              const int* __restrict__ table,
+                              const float* __restrict__ cos_t,
+                              const float* __restrict__ sin_t,
+                              int B, int Hq, int Hk, int D, int W, int P,
+                              int n_pages, int n_pos, long cp, long ch,
+                              long cs) {
+  const int half = D / 2;
+  const int blk8 = half / 8;
+  const int Ht = Hq + 2 * Hk;
+  const long total = (long)B * Ht * blk8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long)gridDim.x * blockDim.x) {
+    const int d8 = (int)(i % blk8);
+    long th = i / blk8;
+    const int h = (int)(th % Ht);
+    const int b = (int)(th / Ht);
+    const int pos = lens[b] - 1;
+    if (pos < 0 || pos >= W * P || pos >= n_pos) continue;
+    const unsigned page =
+        min((unsigned)table[(long)b * W + pos / P], (unsigned)(n_pages - 1));
+    const long row = (long)page * cp + (long)(pos % P) * cs;
+    const int d0 = d8 * 8;
+    ushort_t* src = qkv + ((long)b * Ht + h) * D;
+    const ushortx8 lo = *(const ushortx8*)(src + d0);
+    const ushortx8 hi = *(const ushortx8*)(src + d0 + half);
+    if (h >= Hq + Hk) {
+      ushort_t* dst = pv + row + (long)(h - Hq - Hk) * ch;
+      *(ushortx8*)(dst + d0) = lo;
+      *(ushortx8*)(dst + d0 + half) = hi;
+      continue;
+    }
+    const float* ct = cos_t + (long)pos * half + d0;
+    const float* st = sin_t + (long)pos * half + d0;
+    const floatx4 c0 = *(const floatx4*)ct;
+    const floatx4 c1 = *(const floatx4*)(ct + 4);
+    const floatx4 s0 = *(const floatx4*)st;
+    const floatx4 s1 = *(const floatx4*)(st + 4);
+    ushortx8 olo, ohi;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float c = (e < 4 ? c0[e & 3] : c1[e & 3]);
+      const float sn = (e < 4 ? s0[e & 3] : s1[e & 3]);
+      const float x1 = bf2f(lo[e]);
+      const float x2 = bf2f(hi[e]);
+      olo[e] = f2bf(x1 * c - x2 * sn);
+      ohi[e] = f2bf(x1 * sn + x2 * c);
+    }
+    ushort_t* dst = h < Hq ? src : pk + row + (long)(h - Hq) * ch;
+    *(ushortx8*)(dst + d0) = olo;
+    *(ushortx8*)(dst + d0 + half) = ohi;
+  }
+}
+
+extern "C" void launch_rope_cache_write_paged(
+    void* qkv, void* pk, void* pv, const int* lens, const int* table,
+    const float* cos_t, const float* sin_t, int B, int Hq, int Hk, int D,
+    int W, int P, int n_pages, int n_pos, long cp, long ch, long cs,
+    hipStream_t s) {
+  long total = (long)B * (Hq + 2 * Hk) * (D / 16);
+  long blocks = (total + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(rope_cache_write_paged_kernel, dim3((uint32_t)blocks),
+                     dim3(256), 0, s, (ushort_t*)qkv, (ushort_t*)pk,
+                     (ushort_t*)pv, lens, table, cos_t, sin_t, B, Hq, Hk, D,
+                     W, P, n_pages, n_pos, cp, ch, cs);
+}

@@ -78,6 +78,11 @@ def build_llm_deployment(config: LLMConfig):
             # native engine keeps it opt-in (greedy-only token scheduler)
             continuous=bool(config.engine_kwargs.get(
                 "continuous_batching", False)),
+            # paged KV cache for the continuous engine (opt-in)
+            paged_kv=bool(config.engine_kwargs.get("paged_kv", False)),
+            block_size=int(config.engine_kwargs.get("block_size", 64)),
+            kv_cache_memory_mb=config.engine_kwargs.get(
+                "kv_cache_memory_mb"),
         )
     vllm = _require_vllm()
     from ant_ray_amd import serve

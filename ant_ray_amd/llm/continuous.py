@@ -15,6 +15,20 @@ for a batch-mate to finish.
 Greedy decoding only (the captured step argmaxes on-device), like
 GraphedDecoder. CPU runs the same path eagerly via the ops fallbacks,
 so the scheduler is fully testable without a GPU.
+
+Paged mode (kv_cache="paged"): KV lives in fixed-size token pages
+(models/llama.py PagedKVCache, allocator in llm/kv_blocks.py) reached
+through a device block table [slots, max_pages] that is updated eagerly
+between graph replays, next to lens/cur. A request holds only the pages
+its prompt + max_new_tokens can fill, so long max_seq and many slots no
+longer cost slots x max_seq of memory. Admission RESERVES all of a
+request's pages up front (minus shared prefix pages); when the pool is
+short the request waits, FIFO, until retirements return pages. Because
+nothing admitted can ever run out of pages, no preemption or swap is
+needed. Shared prompt prefixes are mapped by reference (block-table
+entries pointing at the same physical page), not copied. Idle slots sit
+at length 1 on the trash page: the captured step advances lens by a
+device 0/1 active mask instead of clamping at max_seq.
 """
 from __future__ import annotations
 
@@ -25,6 +39,8 @@ from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 import torch
+
+from ant_ray_amd.llm.kv_blocks import plan_admission
 
 
 class _RowCache:
@@ -54,6 +70,7 @@ class _Request:
     # host-side tokens, filled only when stop_ids/on_token force a
     # per-tick readback for this request
     tokens: List[int] = field(default_factory=list)
+    pages: List[int] = field(default_factory=list)  # paged mode only
 
     @property
     def eager_host(self) -> bool:
@@ -128,6 +145,76 @@ class SlotDecoder:
         self._step()
 
 
+class PagedSlotDecoder:
+    """SlotDecoder over a PagedKVCache. Same step/graph protocol; admit()
+    points a slot's table row at its pages and prefills, retire() parks
+    the slot on the trash page. lens advances by the device `active`
+    mask, so idle slots stay at length 1 instead of walking max_seq keys.
+    """
+
+    def __init__(self, model, slots: int, max_seq: int, n_pages: int,
+                 block_size: int, device):
+        from ant_ray_amd.models.llama import PagedKVCache
+
+        self.model = model
+        self.slots = slots
+        self.max_seq = max_seq
+        self.device = device
+        self.cache = PagedKVCache(model.cfg, n_pages, block_size, slots,
+                                  max_seq, device)
+        self.lens = torch.ones(slots, dtype=torch.int32, device=device)
+        self.active = torch.zeros(slots, dtype=torch.int32, device=device)
+        self.cur = torch.zeros(slots, 1, dtype=torch.long, device=device)
+        self.graph = None
+        self._eager_steps = 0
+
+    def admit(self, row: int, tokens: List[int], pages: List[int],
+              hit_tokens: int) -> None:
+        """pages: every page the request may touch, in position order;
+        positions [0, hit_tokens) are already in the shared pages."""
+        view = self.cache.seq_view(pages)
+        toks = torch.tensor([tokens], dtype=torch.long, device=self.device)
+        with torch.no_grad():
+            logits = self.model.forward(
+                toks[:, hit_tokens:] if hit_tokens else toks, cache=view,
+                pos=hit_tokens)
+        tbl = torch.zeros(self.cache.max_pages, dtype=torch.int32)
+        tbl[: len(pages)] = torch.tensor(pages, dtype=torch.int32)
+        self.cache.block_table[row] = tbl.to(self.device)
+        self.cur[row] = logits.argmax(-1)
+        self.lens[row] = len(tokens)
+        self.active[row] = 1
+
+    def retire(self, row: int) -> None:
+        self.active[row] = 0
+        self.lens[row] = 1
+        self.cache.block_table[row] = 0
+
+    def _step(self):
+        lg = self.model.forward(self.cur, cache=self.cache, lens=self.lens)
+        self.cur.copy_(lg.argmax(dim=-1, keepdim=True))
+
+    @torch.no_grad()
+    def step(self) -> None:
+        use_graph = (str(self.device).startswith("cuda")
+                     and self.model.cfg.head_dim == 128)
+        if self.graph is not None:
+            self.graph.replay()
+            return
+        if use_graph and self._eager_steps >= 2:
+            g = torch.cuda.CUDAGraph()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g):
+                self.lens.add_(self.active)
+                self._step()
+            self.graph = g
+            g.replay()
+            return
+        self._eager_steps += 1
+        self.lens.add_(self.active)
+        self._step()
+
+
 class ContinuousLLMEngine:
     """submit() returns a Future; a pump (caller-driven or background
     thread) admits queued requests into free slots and steps all slots
@@ -136,7 +223,12 @@ class ContinuousLLMEngine:
 
     def __init__(self, model_name: str, slots: int = 8, max_seq: int = 4096,
                  seed: int = 0, device: str = "cuda",
-                 start_thread: bool = False):
+                 start_thread: bool = False, kv_cache: str = "contiguous",
+                 block_size: int = 64, kv_pool_mb: Optional[float] = None):
+        """kv_cache: "contiguous" (one slots x max_seq KVCache, the
+        default) or "paged" (page pool of `kv_pool_mb` MiB in
+        `block_size`-token pages; default pool = the contiguous size,
+        slots x max_seq, plus the trash page)."""
         from ant_ray_amd.models import build_model, setup_tunableop
         from ant_ray_amd.models.llama import LlamaForCausalLM
 
@@ -150,10 +242,36 @@ class ContinuousLLMEngine:
         self.model.eval()
         self.device = device
         self.max_seq = max_seq
-        self.dec = SlotDecoder(self.model, slots, max_seq, device)
         from ant_ray_amd.llm.prefix_cache import prefix_cache_from_env
 
-        self.prefix_cache = prefix_cache_from_env()
+        if kv_cache not in ("contiguous", "paged"):
+            raise ValueError(f"kv_cache must be 'contiguous' or 'paged', "
+                             f"got {kv_cache!r}")
+        self.paged = kv_cache == "paged"
+        self.blocks = None
+        if self.paged:
+            from ant_ray_amd.llm.kv_blocks import BlockManager
+            from ant_ray_amd.models.llama import PagedKVCache
+
+            bs = int(block_size)
+            if bs <= 0 or bs % 16:
+                raise ValueError("block_size must be a positive multiple "
+                                 "of 16 (the decode kernel's key stride)")
+            if kv_pool_mb is None:
+                n_pages = slots * -(-max_seq // bs) + 1
+            else:
+                n_pages = int(kv_pool_mb * (1 << 20)
+                              // PagedKVCache.page_bytes(self.model.cfg, bs))
+            self.blocks = BlockManager(n_pages, bs)
+            self.dec = PagedSlotDecoder(self.model, slots, max_seq, n_pages,
+                                        bs, device)
+            # prefix sharing by reference through the page index;
+            # ANTRAY_PREFIX_CACHE=0 disables it like the copy cache
+            self._share = prefix_cache_from_env() is not None
+            self.prefix_cache = None
+        else:
+            self.dec = SlotDecoder(self.model, slots, max_seq, device)
+            self.prefix_cache = prefix_cache_from_env()
         self._ids = itertools.count()
         self._lock = threading.Lock()
         self._queue: List[_Request] = []
@@ -170,10 +288,17 @@ class ContinuousLLMEngine:
             # instantiation costs ~0.7 s — pay it at init, not on the
             # first request)
             try:
-                self.dec.prefill(0, [1, 2, 3])
-                for _ in range(3):
-                    self.dec.step()
-                self.dec.lens.fill_(1)
+                if self.paged:
+                    # warmup on the trash page only (table row stays 0)
+                    self.dec.admit(0, [1, 2, 3], [0], 0)
+                    for _ in range(3):
+                        self.dec.step()
+                    self.dec.retire(0)
+                else:
+                    self.dec.prefill(0, [1, 2, 3])
+                    for _ in range(3):
+                        self.dec.step()
+                    self.dec.lens.fill_(1)
             except Exception:
                 pass
         if start_thread:
@@ -191,6 +316,12 @@ class ContinuousLLMEngine:
         (one batched D2H per step while any such request is active)."""
         if len(prompt_ids) + max_new_tokens > self.max_seq:
             raise ValueError("prompt + max_new_tokens exceeds max_seq")
+        if self.paged:
+            need = self.blocks.pages_needed(len(prompt_ids) + max_new_tokens)
+            if need > self.blocks.total:
+                raise ValueError(
+                    f"request needs {need} KV pages; the whole pool has "
+                    f"{self.blocks.total}")
         req = _Request(next(self._ids), list(prompt_ids),
                        int(max_new_tokens),
                        stop_ids=(frozenset(stop_token_ids)
@@ -213,7 +344,20 @@ class ContinuousLLMEngine:
                     return
                 req = self._queue.pop(0)
             row = free[0]
-            self.dec.prefill(row, req.prompt, self.prefix_cache)
+            if self.paged:
+                plan = plan_admission(self.blocks, req.prompt, req.max_new,
+                                      self._share)
+                if plan is None:  # pool short: wait, keep FIFO order
+                    with self._lock:
+                        self._queue.insert(0, req)
+                    return
+                req.pages, n_hit = plan
+                self.dec.admit(row, req.prompt, req.pages,
+                               n_hit * self.blocks.bs)
+                if self._share:
+                    self.blocks.register(req.prompt, req.pages)
+            else:
+                self.dec.prefill(row, req.prompt, self.prefix_cache)
             req.row = row
             req.start = self._trace_base + len(self._trace)
             req.emitted = 0
@@ -221,6 +365,10 @@ class ContinuousLLMEngine:
 
     def _retire(self, req: _Request) -> None:
         del self._active[req.row]
+        if self.paged:
+            self.dec.retire(req.row)
+            self.blocks.release(req.pages)
+            req.pages = []
         if len(req.tokens) == req.emitted:  # host copy already complete
             req.future.set_result(list(req.tokens))
         else:
@@ -289,6 +437,9 @@ class ContinuousLLMEngine:
 
     def stats(self) -> dict:
         with self._lock:
-            return {"steps": self.steps, "active": len(self._active),
-                    "queued": len(self._queue),
-                    "graph_captured": self.dec.graph is not None}
+            st = {"steps": self.steps, "active": len(self._active),
+                  "queued": len(self._queue),
+                  "graph_captured": self.dec.graph is not None}
+            if self.paged:
+                st.update(self.blocks.stats())
+            return st

@@ -142,7 +142,10 @@ def build_native_llm_deployment(model_name: str = "llama3-8b",
                                 max_seq: int = 4096,
                                 max_batch_size: int = 16,
                                 batch_wait_timeout_s: float = 0.02,
-                                continuous: bool = False):
+                                continuous: bool = False,
+                                paged_kv: bool = False,
+                                block_size: int = 64,
+                                kv_cache_memory_mb: Optional[float] = None):
     """Serve deployment serving the native engine.
 
     continuous=False: dynamic request batching (@serve.batch groups by
@@ -150,11 +153,21 @@ def build_native_llm_deployment(model_name: str = "llama3-8b",
     each request joins the running decode batch immediately
     (llm/continuous.py ContinuousLLMEngine; greedy only).
 
+    paged_kv=True (continuous only): the continuous engine keeps its KV
+    in `block_size`-token pages from a pool of `kv_cache_memory_mb` MiB
+    (default: the contiguous slots x max_seq size), so long max_seq does
+    not cost max_batch_size x max_seq of memory.
+
     Request payload: {"prompt_ids": [int], "max_new_tokens": int,
     "temperature": float} -> {"token_ids": [int]}.
     """
     from ant_ray_amd import serve
 
+    if paged_kv and not continuous:
+        raise ValueError("paged_kv=True requires continuous batching "
+                         "(engine_kwargs continuous_batching=True); the "
+                         "request-batching engine has no paged KV path")
+    kv_cache = "paged" if paged_kv else "contiguous"
     if continuous:
         @serve.deployment(
             num_replicas=num_replicas,
@@ -170,7 +183,8 @@ def build_native_llm_deployment(model_name: str = "llama3-8b",
                 self.engine = ContinuousLLMEngine(
                     model_name, slots=max_batch_size, max_seq=max_seq,
                     device="cuda" if num_gpus > 0 else "cpu",
-                    start_thread=True)
+                    start_thread=True, kv_cache=kv_cache,
+                    block_size=block_size, kv_pool_mb=kv_cache_memory_mb)
 
             async def __call__(self, request: dict) -> dict:
                 import asyncio

@@ -4,8 +4,9 @@ Role parity: vLLM's automatic prefix caching, which the reference exposes
 through its engine kwargs (reference python/ray/llm/_internal/serve/
 engines/vllm/vllm_engine.py:1). Design here is MI355X-native: the decode
 kernels (csrc/kernels/attention_decode.hip) read CONTIGUOUS per-request
-KV caches — 288 GB of HBM3E makes paged physical KV unnecessary at our
-serve shapes — so prefix reuse is done by COPY: cached prompt-prefix KV
+KV caches in the default engines, so prefix reuse is done by COPY (the
+continuous engine's opt-in paged mode shares prefix pages by reference
+instead: llm/kv_blocks.py): cached prompt-prefix KV
 blocks are device-to-device copied into the decoder's contiguous cache
 (a few MB over an ~8 TB/s fabric, microseconds) and only the prompt
 suffix is prefilled (chunked prefill in models/llama.py). What is saved

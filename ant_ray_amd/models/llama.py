@@ -72,6 +72,94 @@ class KVCache:
         return self.k.numel() * 2 * 2
 
 
+class PagedKVCache:
+    """Paged KV cache: page pools [n_layers, n_pages, Hk, P, D] bf16 plus a
+    device block table int32 [slots, W] (layout documented at the top of
+    csrc/kernels/attention_decode.hip). Key t of slot b lives at page
+    block_table[b, t // P], slot t % P. Page 0 is the trash page that
+    every unused table entry points at (llm/kv_blocks.py hands out pages
+    1..n_pages-1). Passed as `cache` together with `lens`, the model runs
+    the paged decode step; per-request prefill goes through seq_view()."""
+
+    paged = True
+
+    def __init__(self, cfg: LlamaConfig, n_pages: int, block_size: int,
+                 slots: int, max_seq: int, device):
+        shape = (cfg.n_layers, n_pages, cfg.n_kv_heads, block_size,
+                 cfg.head_dim)
+        self.k = torch.zeros(shape, device=device, dtype=torch.bfloat16)
+        self.v = torch.zeros(shape, device=device, dtype=torch.bfloat16)
+        self.block_size = block_size
+        self.n_pages = n_pages
+        self.max_seq = max_seq
+        self.max_pages = -(-max_seq // block_size)
+        self.block_table = torch.zeros(slots, self.max_pages,
+                                       dtype=torch.int32, device=device)
+
+    def layer(self, i: int):
+        return self.k[i], self.v[i]
+
+    def seq_view(self, pages) -> "PagedSeqCache":
+        return PagedSeqCache(self, pages)
+
+    def nbytes(self) -> int:
+        return self.k.numel() * 2 * 2
+
+    @staticmethod
+    def page_bytes(cfg: LlamaConfig, block_size: int) -> int:
+        return 2 * cfg.n_layers * cfg.n_kv_heads * block_size \
+            * cfg.head_dim * 2
+
+
+class PagedSeqCache:
+    """One request's pages of a PagedKVCache, for prefill: write() stores a
+    K/V span at its positions (torch index-copy; once per request, not the
+    per-token path) and gather() returns a contiguous [1, Hk, n, D] copy
+    of the first n positions (chunked prefill on a prefix hit). The flat
+    pool-row index of a span is built once and reused by every layer."""
+
+    paged = True
+
+    def __init__(self, cache: PagedKVCache, pages):
+        self.cache = cache
+        self.P = cache.block_size
+        self.pages = torch.as_tensor(pages, dtype=torch.long,
+                                     device=cache.k.device)
+        self._rows = {}
+
+    def _index(self, pos: int, n: int):
+        # rows of the layer pool viewed as [n_pages * Hk * P, D], ordered
+        # [position, head]
+        key = (pos, n)
+        rows = self._rows.get(key)
+        if rows is None:
+            Hk = self.cache.k.shape[2]
+            t = torch.arange(pos, pos + n, device=self.pages.device)
+            base = self.pages[t // self.P] * Hk * self.P + t % self.P
+            h = torch.arange(Hk, device=t.device) * self.P
+            rows = (base[:, None] + h[None, :]).reshape(-1)
+            self._rows[key] = rows
+        return rows
+
+    def write(self, i: int, pos: int, k, v) -> None:
+        # k/v: [1, Hk, S, D] -> pool rows
+        S, D = k.shape[2], k.shape[3]
+        rows = self._index(pos, S)
+        for pool, x in ((self.cache.k[i], k), (self.cache.v[i], v)):
+            pool.view(-1, D).index_copy_(
+                0, rows, x[0].transpose(0, 1).reshape(-1, D))
+
+    def gather(self, i: int, n: int):
+        D = self.cache.k.shape[-1]
+        rows = self._index(0, n)
+        out = []
+        for pool in (self.cache.k[i], self.cache.v[i]):
+            x = pool.view(-1, D).index_select(0, rows)
+            out.append(x.view(n, -1, D).transpose(0, 1).unsqueeze(0)
+                       .contiguous())
+        return out[0], out[1]
+
+
 class GraphedDecoder:
     """Persistent hipGraph-captured greedy decode loop for a FIXED
     (model, batch, cache): capture happens ONCE ever, then every token
@@ -156,8 +244,13 @@ class LlamaAttention(nn.Module):
             # lens buffer (rope + cache write + flash-decode in one call —
             # no host scalar depends on the step index)
             ck, cv = cache.layer(layer_idx)
-            o = ops.decode_step_attn(qkv.view(B, (Hq + 2 * Hk) * D), ck, cv,
-                                     lens, cos, sin, Hq, Hk)
+            if getattr(cache, "paged", False):
+                o = ops.decode_step_attn_paged(
+                    qkv.view(B, (Hq + 2 * Hk) * D), ck, cv,
+                    cache.block_table, lens, cos, sin, Hq, Hk)
+            else:
+                o = ops.decode_step_attn(qkv.view(B, (Hq + 2 * Hk) * D), ck,
+                                         cv, lens, cos, sin, Hq, Hk)
             return self.wo(o.view(B, 1, Hq * D))
         if (cache is None and qkv.is_cuda and D == 128
                 and torch.is_grad_enabled() and qkv.requires_grad
@@ -175,10 +268,22 @@ class LlamaAttention(nn.Module):
         q = qkv[..., : Hq * D].view(B, S, Hq, D).transpose(1, 2)
         k = qkv[..., Hq * D : (Hq + Hk) * D].view(B, S, Hk, D).transpose(1, 2)
         v = qkv[..., (Hq + Hk) * D :].view(B, S, Hk, D).transpose(1, 2)
-        if cache is not None:
+        paged_fresh = False
+        if cache is not None and getattr(cache, "paged", False):
+            # paged prefill: the prompt's K/V goes into the request's
+            # pages; a prefix hit gathers the pages into a temporary
+            # contiguous buffer for the chunked-prefill path below, a cold
+            # prompt attends over k/v straight from qkv
+            cache.write(layer_idx, pos, k, v)
+            if pos > 0:
+                ck, cv = cache.gather(layer_idx, pos + S)
+            else:
+                paged_fresh = True
+        elif cache is not None:
             ck, cv = cache.layer(layer_idx)
             ck[:, :, pos : pos + S] = k
             cv[:, :, pos : pos + S] = v
+        if cache is not None and not paged_fresh:
             if S == 1:
                 # single-token decode over the cache (flash-decode kernel)
                 o = ops.attention_decode(q.reshape(B, Hq, D), ck, cv,

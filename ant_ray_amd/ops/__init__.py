@@ -14,9 +14,11 @@ from ant_ray_amd.ops.functional import (  # noqa: F401
     adamw_step,
     attention,
     attention_decode,
+    attention_decode_paged,
     cast_affine,
     chunked_prefill_attention,
     decode_step_attn,
+    decode_step_attn_paged,
     fused_add_rmsnorm,
     nhwc_to_nchw,
     rmsnorm,

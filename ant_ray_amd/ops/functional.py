@@ -365,6 +365,64 @@ def decode_step_attn(qkv: torch.Tensor, ck: torch.Tensor, cv: torch.Tensor,
                                     scale=float(scale))
 
 
+def attention_decode_paged(q: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, block_table: torch.Tensor,
+                           lens: torch.Tensor, scale=None) -> torch.Tensor:
+    """Paged flash-decode (attention_decode.hip, PAGED instantiation):
+    q [B,Hq,D]; one layer's pools [n_pages,Hk,P,D]; block_table int32
+    [B,W]; lens int32 [B]. Pool layout is documented at the top of
+    csrc/kernels/attention_decode.hip. CPU fallback: exact fp32
+    reference over the gathered pages."""
+    if scale is None:
+        scale = q.shape[-1] ** -0.5
+    if _use_hip(q):
+        return _hip().attn_decode_paged(q.contiguous(), k_pool, v_pool,
+                                        block_table, lens, float(scale))
+    return ref.attention_decode_paged_ref(q, k_pool, v_pool, block_table,
+                                          lens, scale=float(scale))
+
+
+def decode_step_attn_paged(qkv: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, block_table: torch.Tensor,
+                           lens: torch.Tensor, cos: torch.Tensor,
+                           sin: torch.Tensor, hq: int, hk: int,
+                           scale=None) -> torch.Tensor:
+    """decode_step_attn over a PAGED cache: rope q/k, write the new K/V
+    row at page block_table[b, pos//P] slot pos%P (pos = lens[b]-1), then
+    paged flash-decode — one graph-capturable call. CPU fallback: exact
+    fp32 reference."""
+    D = k_pool.shape[-1]
+    if scale is None:
+        scale = D ** -0.5
+    if _use_hip(qkv):
+        return _hip().decode_step_attn_paged(qkv, k_pool, v_pool,
+                                             block_table, lens, cos, sin,
+                                             hq, hk, float(scale))
+    B = qkv.shape[0]
+    P = k_pool.shape[2]
+    flat = qkv.reshape(B, -1)
+    q = flat[:, : hq * D].view(B, hq, D)
+    k = flat[:, hq * D : (hq + hk) * D].view(B, hk, D)
+    v = flat[:, (hq + hk) * D :].view(B, hk, D)
+    pos = (lens.long() - 1).clamp(min=0)
+    half = D // 2
+    c = cos[pos].view(B, 1, half).float()
+    s = sin[pos].view(B, 1, half).float()
+
+    def rot(x):
+        xf = x.float()
+        x1, x2 = xf[..., :half], xf[..., half:]
+        return torch.cat([x1 * c - x2 * s, x1 * s + x2 * c], -1).to(x.dtype)
+
+    q, k = rot(q), rot(k)
+    rows = torch.arange(B, device=qkv.device)
+    pages = block_table.long()[rows, pos // P]
+    k_pool[pages, :, pos % P] = k
+    v_pool[pages, :, pos % P] = v
+    return ref.attention_decode_paged_ref(q, k_pool, v_pool, block_table,
+                                          lens, scale=float(scale))
+
+
 # ------------------------------------------------------- data transforms
 
 

@@ -94,6 +94,26 @@ def attention_decode_ref(q, k, v, lens=None, scale=None):
     return torch.einsum("bht,bhtd->bhd", p, vf).to(q.dtype)
 
 
+def gather_pages(pool, block_table):
+    """Contiguous view of a paged cache: pool [n_pages, Hk, P, D] (one
+    layer; layout in csrc/kernels/attention_decode.hip), block_table int
+    [B, W] -> [B, Hk, W*P, D] (key t of row b = page table[b, t//P], slot
+    t%P)."""
+    n_pages, Hk, P, D = pool.shape
+    B, W = block_table.shape
+    g = pool[block_table.long()]                    # [B, W, Hk, P, D]
+    return g.permute(0, 2, 1, 3, 4).reshape(B, Hk, W * P, D)
+
+
+def attention_decode_paged_ref(q, k_pool, v_pool, block_table, lens,
+                               scale=None):
+    """fp32 reference paged decode: gathers each row's pages into
+    contiguous K/V and runs attention_decode_ref."""
+    k = gather_pages(k_pool, block_table)
+    v = gather_pages(v_pool, block_table)
+    return attention_decode_ref(q, k, v, lens=lens, scale=scale)
+
+
 def attention_ref(q, k, v, causal=True, scale=None):
     """fp32 reference attention with GQA (q:[B,Hq,S,D], k/v:[B,Hk,S,D])."""
     import torch
